@@ -23,6 +23,9 @@ Same JSON line (rank 0, N = 1): `roofline` (dominant GEMM kernel, live HIP-event
 on the host cores, bounded sample: all cores and one thread), `decode` (NA mask-predict + coarse templates, with its
 own roofline and CPU baseline), `train_L30` (the reference's MSRVTT default length), `config1_nab_bf16`,
 `nacf_bf16`, `config5_ar_vs_na`, `loader_fed`.
+
+--dump-outputs DIR writes what the timed steps leave their caller, taken right after the last of them (dump_outputs):
+weights, batch and dropout stream are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import glob
@@ -131,6 +134,35 @@ def timed_steps(engine, n, barrier=None):
         engine()
     (barrier or torch.cuda.synchronize)()
     return time.perf_counter() - t0
+
+
+DUMP_SAMPLE = 1 << 23       # elements kept of an array larger than that (32 MB of fp32: every dump stays far below 64 MB)
+
+
+def sample_flat(x, limit=DUMP_SAMPLE, seed=0):
+    """x flattened, whole if it has at most `limit` elements, else `limit` of them at seeded positions in ascending order:
+    the same positions for every array of the same length, whatever build or run wrote it"""
+    x = x.reshape(-1)
+    if x.numel() <= limit:
+        return x
+    idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(seed))[:limit].sort().values
+    return x[idx.to(x.device)]
+
+
+def dump_outputs(path, engine, model, crit):
+    """What a caller of the timed path holds after its last step, as <path>/<name>.npy (fp32 / fp64):
+      loss       [1]  the step's loss (TrainStep.loss)
+      params     [n]  the model's parameters after the step's Adam update, model.parameters() order, concatenated (sample_flat)
+      loss_info  [k]  Criterion.get_loss_info(): the running meters (losses, word accuracies, perplexity) over every step so far"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        params = sample_flat(torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+    arrays = {"loss": engine.loss.detach().reshape(1).float().cpu().numpy(),
+              "params": params.float().cpu().numpy(),
+              "loss_info": np.asarray(crit.get_loss_info()[1], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def median_step_ms(engine, min_seconds=1.0, max_steps=400):
@@ -516,6 +548,8 @@ def main():
     ap.add_argument("--no-compare", action="store_true", help="skip the extra legs (config 1 bf16, NACF bf16, L=30, config 5)")
     ap.add_argument("--no-loader", action="store_true", help="skip the shard-loader leg (SURVEY 8f row 1)")
     ap.add_argument("--loader-videos", type=int, default=1024, help="videos in the synthetic feature shards")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (loss, updated parameters, meters) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.decode_only:      # (what tools/collect_profiles.sh profiles as the decode-only set)
         args.no_compare = args.no_loader = args.no_cpu_baseline = True
@@ -582,6 +616,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     videos_per_s = B * world * args.steps / dt
     final_loss = float(engine.loss)
+    if args.dump_outputs and rank == 0:         # before anything below steps the engine again
+        dump_outputs(args.dump_outputs, engine, model, crit)
     rank_losses = None
     if multi:                                   # every rank's loss (different shards: all must be finite and close)
         ls = [torch.zeros(1, device=dev) for _ in range(world)]

@@ -32,6 +32,34 @@ def test_bench_prints_one_contract_line(dev):
     assert d["decode"]["captions_per_s"] > 100
 
 
+def test_dump_outputs_of_the_last_timed_step_repeat_run_to_run(dev, tmp_path):
+    """--dump-outputs: loss, parameters after the last timed step and the meters as fp32 / fp64 .npy, at most 64 MB in all, and
+    -- seeded weights, batch and dropout stream -- the same bits from two runs with the same arguments; --steps sets how many
+    steps ran before the dump (one step more moves the weights)"""
+    import numpy as np
+
+    def run(tag, steps):
+        d = str(tmp_path / tag)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "2", "--no-compare",
+                              "--no-loader", "--no-decode", "--no-cpu-baseline", "--dump-outputs", d],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.strip().splitlines() if l.strip()][-1])
+        assert line["steps"] == steps
+        return line, {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    line, a = run("a", 4)
+    _, b = run("b", 4)
+    _, c = run("c", 5)
+    assert sorted(a) == ["loss", "loss_info", "params"]
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["params"].size == 1 << 23                  # the seeded sample of the ~18 M parameters
+    assert abs(float(a["loss"][0]) - line["final_loss"]) < 1e-3
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert float(np.abs(a["params"] - c["params"]).max()) > 1e-5
+
+
 def test_multi_rank_launch_sequence_with_one_rank_group(dev):
     """NACF_BENCH_FORCE_DIST=1 runs the N > 1 step (two backward graphs, bucketed RCCL all-reduces on their own stream,
     Adam per bucket) with a 1-rank process group: it must capture, and train exactly like the single-graph step"""

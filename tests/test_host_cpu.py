@@ -162,3 +162,26 @@ def test_reference_checkpoint_contract(tmp_path):
                     filepath=str(tmp_path), filename="c.pth.tar")
     m2, o2 = load_model_and_opt(os.path.join(str(tmp_path), "best.pth.tar"), "cpu")
     assert all(torch.equal(v, after[k]) for k, v in m2.state_dict().items())
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: one .npy per array in fp32 / fp64, parameters in model.parameters() order; an array above the
+    cap is cut to the same seeded positions on every call"""
+    import types
+    import numpy as np
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(5, 3), torch.nn.Linear(3, 2))
+    engine = types.SimpleNamespace(loss=torch.tensor(1.25))
+    crit = types.SimpleNamespace(get_loss_info=lambda: (["a", "b"], [0.5, 2.0]))
+    bench.dump_outputs(str(tmp_path / "d"), engine, model, crit)
+    got = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(str(tmp_path / "d")))}
+    assert sorted(got) == ["loss", "loss_info", "params"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["loss"].tolist() == [1.25] and got["loss_info"].tolist() == [0.5, 2.0]
+    want = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    assert got["params"].dtype == np.float32 and np.array_equal(got["params"], want)
+    x = torch.arange(1000, dtype=torch.float32)
+    a, b = bench.sample_flat(x, limit=64), bench.sample_flat(x.clone(), limit=64)
+    assert a.numel() == 64 and torch.equal(a, b) and len(set(a.tolist())) == 64 and bool((a[1:] > a[:-1]).all())
+    assert torch.equal(bench.sample_flat(x, limit=1000), x)
+    assert bench.DUMP_SAMPLE * 4 + (1 << 20) <= 64 << 20          # params at the cap + the small arrays: below 64 MB
