@@ -465,7 +465,10 @@ int nacf_layernorm_bwd(const float* dOut, const float* xhat, const float* rstd, 
  * tokens; key masked when token == PAD, models/Decoder.py:13-22);
  * causal != 0 adds the strict upper-triangular mask (models/Decoder.py:24-39); causal = 1 + w with w > 0 also masks the
  * keys k <= q - w (--watch w, models/Decoder.py:27-29: a query sees itself and the w - 1 tokens before it).
- * probs: optional [H, R, Lq, Lk] output (models/bert.py:179). */
+ * probs: optional [H, R, Lq, Lk] output (models/bert.py:179).
+ * Shapes: matrix-core kernels for dk = 16 / 64 with Lq <= 32 per block of queries and Lk <= 128; cross-attention (no key_tokens,
+ * not causal) at dk = 64 over ANY Lk > 128 on the streaming kernels (forward: any Lq; backward: Lq <= 32); everything else on
+ * the LDS-tile kernels, whose tile must fit 160 KB of LDS (NACF_EUNSUPPORTED names the limit). */
 int nacf_attention_fwd(const float* Q, int64_t ldq, const float* K, int64_t ldk,
                        const float* V, int64_t ldv, float* O, int64_t ldo,
                        const int64_t* key_tokens, int causal, float* probs,

@@ -978,4 +978,433 @@ __global__ __launch_bounds__(256, 2) void fwd_lds_kernel(const float* __restrict
   fwd_lds_item<DK16, PR>((int)blockIdx.x, smem, Q, ldq, K, ldk, V, ldv, O, ldo, R, H, Lq, Lk, kv_div, kv_mod, rounds);
 }
 
+
+// ---- streaming kernels (cross-attention: no key mask, not causal, dk = 64, MORE than 128 keys) -------------------------
+// Three- and four-modality memories (M = modalities x frames keys) and long clips.  The kernels above have 128 keys in their
+// register / LDS geometry; these walk the memory in blocks of 128 keys and carry the soft-max statistics across blocks.
+constexpr int FS_KEYS = 64;                      // keys per block of the forward (see fwd_stream_kernel for why not 128)
+// a block's K and V rows for the whole workgroup: KEYS / 16 wide loads per thread and operand at dk = 64, ALL requested before anything
+// waits on them (rows past the memory's end re-read its last row: never live keys, and never uninitialised LDS either)
+template <int DK16, int KEYS>
+__device__ __forceinline__ void stream_load(f32x4 (&kr)[KEYS * DK16 / 64], f32x4 (&vr)[KEYS * DK16 / 64], const float* __restrict__ Kg,
+                                            int64_t ldk, const float* __restrict__ Vg, int64_t ldv, int k0, int Lk) {
+  constexpr int VPR = 4 * DK16;                  // f32x4 per row
+#pragma unroll
+  for (int u = 0; u < KEYS * DK16 / 64; ++u) {
+    const int q = threadIdx.x + 256 * u;
+    const int row = min(k0 + q / VPR, Lk - 1), c = (q % VPR) * 4;
+    kr[u] = *reinterpret_cast<const f32x4*>(Kg + (int64_t)row * ldk + c);
+    vr[u] = *reinterpret_cast<const f32x4*>(Vg + (int64_t)row * ldv + c);
+  }
+}
+template <int DK16, int KEYS>
+__device__ __forceinline__ void stream_store(float* Ks, float* Vs, const f32x4 (&kr)[KEYS * DK16 / 64],
+                                             const f32x4 (&vr)[KEYS * DK16 / 64]) {
+  constexpr int VPR = 4 * DK16;
+#pragma unroll
+  for (int u = 0; u < KEYS * DK16 / 64; ++u) {
+    const int q = threadIdx.x + 256 * u;
+    const int row = q / VPR, c = (q % VPR) * 4;
+    *reinterpret_cast<f32x4*>(&Ks[row * FL_PITCH + c]) = kr[u];
+    *reinterpret_cast<f32x4*>(&Vs[row * FL_PITCH + c]) = vr[u];
+  }
+}
+
+// Forward.  Ownership of fwd_lds_kernel: one workgroup per (memory row set, head), each wave an item = (sequence of the row set,
+// block of 32 queries).  K and V pass through LDS in blocks of FS_KEYS keys (the FL_PITCH image and the contract_d / contract_key
+// fragment layouts of fwd_lds_kernel, per block).  Register staging: the NEXT block's global loads are requested before the waves
+// start on the current block and are written to the other of two LDS images after it, so one barrier per block orders both the
+// image just written and the image about to be overwritten.  Blocks are 64 keys, not 128: with 128 the 64 staging registers stay
+// live across a block's 64 score registers, the query fragments and the accumulator, and the compiler spills 213 VGPRs at the
+// budget of two workgroups per CU (docs/experiments.md); with 64 both halve and two images of K and V are the 68 KiB one 128-key
+// image was.  LDS 2 x 2 x 64 x FL_PITCH floats = 68 KiB and launch_bounds(256, 2): two workgroups per CU on both counts.
+// A wave keeps the running row maximum m, the running sum l of exp(S - m) and the unnormalised fp32 accumulator o across blocks
+// (o and l are rescaled by exp(m_old - m_new) when a block raises the maximum) and divides once at the end.  PR = 1 rounds the
+// unnormalised block probabilities exp(S - m) to bf16, where the one-block kernels round the normalised ones.  Row sets with more
+// than four items are served four items at a time, the blocks streamed again per group (from L2): a wave never holds the state
+// of two items.  PROBS (the decoder's output_attentions, an analysis path): a second sweep recomputes S and stores
+// exp(S - m) / l with the final statistics; an instantiation of its own, so that the timed one carries none of it.
+template <int DK16, int PR = 0, bool PROBS = false>
+__global__ __launch_bounds__(256, 2) void fwd_stream_kernel(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ K,
+                                                             int64_t ldk, const float* __restrict__ V, int64_t ldv,
+                                                             float* __restrict__ O, int64_t ldo, float* __restrict__ probs, int R,
+                                                             int n_kv, int H, int Lq, int Lk, int kv_div, int kv_mod, int rounds) {
+  constexpr int DK = 16 * DK16;
+  constexpr int NKT = FS_KEYS / 16;
+  constexpr int IMG = 2 * FS_KEYS * FL_PITCH;     // floats of one image: K block, V block
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int kvr = blockIdx.x / H, h = blockIdx.x % H;
+  const int i = lane & 15, g = lane >> 4;
+  const float* Kg = K + (int64_t)kvr * Lk * ldk + h * DK;
+  const float* Vg = V + (int64_t)kvr * Lk * ldv + h * DK;
+  const int nqb = (Lq + 31) / 32;
+  const int n_items = rounds * nqb;               // (k-th sequence of the row set, block of 32 queries)
+  const int n_groups = (n_items + 3) / 4;
+  const int n_blocks = (Lk + FS_KEYS - 1) / FS_KEYS;
+  constexpr int n_sweeps = PROBS ? 2 : 1;
+  const float sq = sqrtf((float)DK);
+  int buf = 0;                                    // image of the block about to be worked on
+  {
+    f32x4 kr[FS_KEYS * DK16 / 64], vr[FS_KEYS * DK16 / 64];
+    stream_load<DK16, FS_KEYS>(kr, vr, Kg, ldk, Vg, ldv, 0, Lk);
+    stream_store<DK16, FS_KEYS>(smem, smem + FS_KEYS * FL_PITCH, kr, vr);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int grp = 0; grp < n_groups; ++grp) {
+    const int it = grp * 4 + wave;
+    const int k = it / nqb, qb = it % nqb;
+    const int r = ((k / kv_div) * kv_mod + kvr) * kv_div + k % kv_div;
+    const bool has = it < n_items && r < R && (k / kv_div) * kv_mod + kvr < (R + kv_div - 1) / kv_div;   // uniform over the wave
+    const int q0 = qb * 32;
+    const int nq = min(32, Lq - q0);
+    f32x4 qf[2][DK16], o[2][DK16];
+    float m[2] = {-3.0e38f, -3.0e38f}, l[2] = {0.f, 0.f};
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int td = 0; td < DK16; ++td) { qf[tm][td] = f32x4{0.f, 0.f, 0.f, 0.f}; o[tm][td] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    if (has) {
+      const float* Qb = Q + ((int64_t)r * Lq + q0) * ldq + h * DK;
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm) load_row_frag<DK16>(qf[tm], Qb, ldq, tm * 16 + i, nq, g);
+    }
+#pragma unroll 1
+    for (int sweep = 0; sweep < n_sweeps; ++sweep) {
+#pragma unroll 1
+      for (int b = 0; b < n_blocks; ++b) {
+        const float* Ks = smem + buf * IMG;
+        const float* Vs = Ks + FS_KEYS * FL_PITCH;
+        const bool more = b + 1 < n_blocks || sweep + 1 < n_sweeps || grp + 1 < n_groups;
+        f32x4 kr[FS_KEYS * DK16 / 64], vr[FS_KEYS * DK16 / 64];
+        if (more)                                 // in flight while this block is worked on
+          stream_load<DK16, FS_KEYS>(kr, vr, Kg, ldk, Vg, ldv, b + 1 < n_blocks ? (b + 1) * FS_KEYS : 0, Lk);
+        __builtin_amdgcn_sched_barrier(0);        // (the scheduler would sink the loads to their stores)
+        if (has) {
+          const int k0 = b * FS_KEYS;
+          const int nk = min(FS_KEYS, Lk - k0);   // live keys of this block
+          f32x4 sc[2][NKT];
+#pragma unroll
+          for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < NKT; ++tn) sc[tm][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+          contract_d<NKT, DK16, PR>(sc, Ks, FL_PITCH, nk, qf, i, g);
+          if (PROBS && sweep == 1) {
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) {
+              const int q = tm * 16 + i;
+              if (q < nq) {
+                float* prow = probs + (((int64_t)h * R + r) * Lq + q0 + q) * Lk + k0;
+#pragma unroll
+                for (int tn = 0; tn < NKT; ++tn)
+#pragma unroll
+                  for (int rr = 0; rr < 4; ++rr) {
+                    const int key = tn * 16 + g * 4 + rr;
+                    if (key < nk) prow[key] = expf(sc[tm][tn][rr] / sq - m[tm]) / l[tm];
+                  }
+              }
+            }
+          } else {
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) {
+              float mx = -3.0e38f;
+#pragma unroll
+              for (int tn = 0; tn < NKT; ++tn)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                  const int key = tn * 16 + g * 4 + rr;
+                  const float v = key < nk ? sc[tm][tn][rr] / sq : -3.0e38f;      // tile padding: contributes exactly 0
+                  sc[tm][tn][rr] = v;
+                  mx = fmaxf(mx, v);
+                }
+              mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+              mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+              const float m_new = fmaxf(m[tm], mx);
+              const float alpha = expf(m[tm] - m_new);                            // first block: exp(-3e38 - m_new) = 0
+              float sum = 0.f;
+#pragma unroll
+              for (int tn = 0; tn < NKT; ++tn)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                  const float e = expf(sc[tm][tn][rr] - m_new);
+                  sc[tm][tn][rr] = e;
+                  sum += e;
+                }
+              sum += __shfl_xor(sum, 16, 64);
+              sum += __shfl_xor(sum, 32, 64);
+              l[tm] = l[tm] * alpha + sum;
+              m[tm] = m_new;
+#pragma unroll
+              for (int td = 0; td < DK16; ++td) o[tm][td] *= alpha;
+            }
+            contract_key<NKT, DK16, PR>(o, sc, Vs, FL_PITCH, nk, i, g);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {                               // the other image: last read one block ago, before the barrier that ended it
+          float* Kn = smem + (buf ^ 1) * IMG;
+          stream_store<DK16, FS_KEYS>(Kn, Kn + FS_KEYS * FL_PITCH, kr, vr);
+        }
+        __syncthreads();
+        buf ^= 1;
+      }
+      if (has && sweep == 0) {
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+          for (int td = 0; td < DK16; ++td) o[tm][td] /= l[tm];
+        store_rows<DK16>(o, O + ((int64_t)r * Lq + q0) * ldo + h * DK, ldo, nq, i, g);
+      }
+    }
+  }
+}
+
+// S block and dP block of one wave (32 keys x 32 queries) with the branch-free batched operand loads of bwd_kb_kernel<.., NB = 1>
+template <int DK16, int PR>
+__device__ __forceinline__ void kb_scores(f32x4 (&p)[2][2], f32x4 (&dp)[2][2], const float* __restrict__ Qb, int64_t ldq,
+                                          const float* __restrict__ dOb, int64_t lddo, const float* __restrict__ Kb, int64_t ldk,
+                                          const float* __restrict__ Vb, int64_t ldv, int Lq, int nk, int i, int g) {
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) { p[tm][t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[tm][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  {
+    f32x4 qf[2][DK16], kf[2][DK16];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      raw_row_frag<DK16>(qf[t], Qb, ldq, t * 16 + i, Lq, g);
+      raw_row_frag<DK16>(kf[t], Kb, ldk, t * 16 + i, nk, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) { mask_row_frag<DK16>(qf[t], t * 16 + i < Lq); mask_row_frag<DK16>(kf[t], t * 16 + i < nk); }
+    contract_d_regs<2, DK16, PR>(p, kf, qf);                          // S block
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  {
+    f32x4 gf[2][DK16], vf[2][DK16];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      raw_row_frag<DK16>(gf[t], dOb, lddo, t * 16 + i, Lq, g);
+      raw_row_frag<DK16>(vf[t], Vb, ldv, t * 16 + i, nk, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) { mask_row_frag<DK16>(gf[t], t * 16 + i < Lq); mask_row_frag<DK16>(vf[t], t * 16 + i < nk); }
+    contract_d_regs<2, DK16, PR>(dp, vf, gf);                         // dP block = dO V_blk^T
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Backward, the long-memory form of bwd_kb_kernel.  One workgroup per (memory row set, head); Lq <= 32 per sequence (training
+// never merges candidates: longer sequences are left to the generic kernel and its limit).  Deterministic: no atomics, every
+// sum in a fixed order.
+//   1. statistics pre-pass, per sequence over all chunks of 128 keys (S and dP only): each wave carries the row maximum, the
+//      sum of exp(S - max) and the sum of exp(S - max) * dP of ITS 32-key blocks with flash-style rescaling; the four waves'
+//      triples are then combined in wave order into (M, L, delta = rowsum(P * dP)) kept in LDS per (sequence, query row).
+//   2. outer loop over chunks, inner loop over the sequences of the row set: inside a chunk the four waves own 32 keys each
+//      exactly as in bwd_kb_kernel -- P and dS of the block from the stored statistics, dK / dV of the chunk accumulated in
+//      registers over the sequences and stored once, with plain stores.  dQ of a sequence is the sum over chunks: the four
+//      waves' partials are combined through LDS as before, the first chunk stores, later chunks add (load + add + store by the
+//      same thread at the same address, chunk order fixed).
+// Seven contractions per key (S and dP twice) where a backward that is handed the forward's log-sum-exp needs five; that would
+// change the autograd node and the C ABI.  LDS: 3 x 4 x 32 exchange + dQ partials [4][32][KB_RED_PITCH] + transpose tiles
+// [4][32][KB_PITCH] (NOT aliased here: one barrier less per sequence and chunk) + statistics [rounds][3][32] = 59.5 KiB + 384 B
+// per sequence: two workgroups per CU, the register budget of launch_bounds, up to 48 sequences per row set.
+template <int DK16, int PR = 0>
+__global__ __launch_bounds__(256, KB_WGS) void bwd_kb_stream_kernel(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ K,
+                                                             int64_t ldk, const float* __restrict__ V, int64_t ldv,
+                                                             const float* __restrict__ dO, int64_t lddo, float* __restrict__ dQ,
+                                                             int64_t lddq, float* __restrict__ dK, int64_t lddk,
+                                                             float* __restrict__ dV, int64_t lddv, int R, int n_kv, int H, int Lq,
+                                                             int Lk, int kv_div, int kv_mod, int rounds) {
+  constexpr int DK = 16 * DK16;
+  static_assert(DK <= 64, "dQ reduce buffer is sized for dk <= 64");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* ex = smem;                                             // [3][4][32]: a wave's max, sum, sum * dP over its blocks
+  float* red = ex + 3 * 4 * 32;                                 // [4][32][KB_RED_PITCH] dQ partials
+  float* T = red + 4 * 32 * KB_RED_PITCH + wave * 32 * KB_PITCH; // wave-private transpose tile
+  float* stat = red + 4 * 32 * KB_RED_PITCH + 4 * 32 * KB_PITCH; // [rounds][3][32]: M, L, delta
+  const int kvr = blockIdx.x / H, h = blockIdx.x % H;
+  int i = lane & 15, g = lane >> 4;
+  const float sq = sqrtf((float)DK);
+  const int n_chunks = (Lk + 127) / 128;
+  const float* Kh = K + (int64_t)kvr * Lk * ldk + h * DK;
+  const float* Vh = V + (int64_t)kvr * Lk * ldv + h * DK;
+
+  for (int k = 0; k < rounds; ++k) {
+    // the k-th sequence of this memory row set (same enumeration as bwd_kernel); uniform over the workgroup
+    const int r = ((k / kv_div) * kv_mod + kvr) * kv_div + k % kv_div;
+    if (!(r < R && (k / kv_div) * kv_mod + kvr < (R + kv_div - 1) / kv_div)) continue;
+    const float* Qb = Q + (int64_t)r * Lq * ldq + h * DK;
+    const float* dOb = dO + (int64_t)r * Lq * lddo + h * DK;
+    float wm[2] = {-3.0e38f, -3.0e38f}, wl[2] = {0.f, 0.f}, wd[2] = {0.f, 0.f};
+    for (int c = 0; c < n_chunks; ++c) {
+      const int k0 = c * 128 + wave * 32;
+      const int nk = max(0, min(32, Lk - k0));                  // live keys of this wave's block
+      if (nk == 0) continue;
+      f32x4 p[2][2], dp[2][2];
+      kb_scores<DK16, PR>(p, dp, Qb, ldq, dOb, lddo, Kh + (int64_t)k0 * ldk, ldk, Vh + (int64_t)k0 * ldv, ldv, Lq, nk, i, g);
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm) {
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int key = t * 16 + g * 4 + rr;
+            const float v = key < nk ? p[tm][t][rr] / sq : -3.0e38f;
+            p[tm][t][rr] = v;
+            mx = fmaxf(mx, v);
+          }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(wm[tm], mx);
+        const float alpha = expf(wm[tm] - m_new);
+        float sum = 0.f, dsum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const float e = expf(p[tm][t][rr] - m_new);            // tile padding: exp(-3e38 - m) = 0
+            sum += e;
+            dsum += e * dp[tm][t][rr];
+          }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        dsum += __shfl_xor(dsum, 16, 64);
+        dsum += __shfl_xor(dsum, 32, 64);
+        wl[tm] = wl[tm] * alpha + sum;
+        wd[tm] = wd[tm] * alpha + dsum;
+        wm[tm] = m_new;
+      }
+    }
+    if (g == 0) {
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm) {
+        ex[(0 * 4 + wave) * 32 + tm * 16 + i] = wm[tm];
+        ex[(1 * 4 + wave) * 32 + tm * 16 + i] = wl[tm];
+        ex[(2 * 4 + wave) * 32 + tm * 16 + i] = wd[tm];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32) {
+      const int q = threadIdx.x;
+      float M = -3.0e38f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) M = fmaxf(M, ex[(0 * 4 + w) * 32 + q]);
+      float Lsum = 0.f, Dsum = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float sc = expf(ex[(0 * 4 + w) * 32 + q] - M);    // a wave without live keys: exp(-3e38 - M) = 0
+        Lsum += ex[(1 * 4 + w) * 32 + q] * sc;
+        Dsum += ex[(2 * 4 + w) * 32 + q] * sc;
+      }
+      stat[(k * 3 + 0) * 32 + q] = M;
+      stat[(k * 3 + 1) * 32 + q] = Lsum;
+      stat[(k * 3 + 2) * 32 + q] = Dsum / Lsum;
+    }
+    __syncthreads();                                            // stat is read below, ex rewritten by the next sequence
+  }
+
+  for (int c = 0; c < n_chunks; ++c) {
+    const int k0 = c * 128 + wave * 32;
+    const int nk = max(0, min(32, Lk - k0));
+    const float* Kb = Kh + (int64_t)k0 * ldk;
+    const float* Vb = Vh + (int64_t)k0 * ldv;
+    f32x4 accK[DK16][2], accV[DK16][2];
+#pragma unroll
+    for (int td = 0; td < DK16; ++td)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) { accK[td][t] = f32x4{0.f, 0.f, 0.f, 0.f}; accV[td][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int k = 0; k < rounds; ++k) {
+      const int r = ((k / kv_div) * kv_mod + kvr) * kv_div + k % kv_div;
+      if (!(r < R && (k / kv_div) * kv_mod + kvr < (R + kv_div - 1) / kv_div)) continue;
+      const float* Qb = Q + (int64_t)r * Lq * ldq + h * DK;
+      const float* dOb = dO + (int64_t)r * Lq * lddo + h * DK;
+      // Every per-lane operand address below is invariant over both loops; hoisted to the kernel's entry they are some 60 registers
+      // of 64-bit offsets held across everything, and 12 of them spill at this budget (52 B of scratch).  Opaque lane indices make
+      // each sequence recompute its addresses (a few dozen VALU operations): 197 / 204 VGPRs, no scratch.
+      asm volatile("" : "+v"(i), "+v"(g));
+      f32x4 p[2][2], dp[2][2];
+      if (nk > 0) {
+        kb_scores<DK16, PR>(p, dp, Qb, ldq, dOb, lddo, Kb, ldk, Vb, ldv, Lq, nk, i, g);
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+          const int q = tm * 16 + i;
+          const float M = stat[(k * 3 + 0) * 32 + q], Lsum = stat[(k * 3 + 1) * 32 + q], dot = stat[(k * 3 + 2) * 32 + q];
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int key = t * 16 + g * 4 + rr;
+              const float pv = key < nk ? expf(p[tm][t][rr] / sq - M) / Lsum : 0.f;
+              p[tm][t][rr] = pv;                                               // P block
+              dp[tm][t][rr] = pv * (dp[tm][t][rr] - dot) / sq;                 // dS block
+            }
+        }
+      }
+      {
+        f32x4 o[2][DK16];
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+          for (int td = 0; td < DK16; ++td) o[tm][td] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (nk > 0) contract_key<2, DK16, PR>(o, dp, Kb, ldk, nk, i, g);      // dQ partial = dS_blk K_blk
+        __syncthreads();                                        // the previous reduction has read every partial
+        float* mine = red + wave * 32 * KB_RED_PITCH;
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            float v[DK16];
+#pragma unroll
+            for (int td = 0; td < DK16; ++td) v[td] = o[tm][td][rr];
+            Ld<DK16>::st(mine + (tm * 16 + i) * KB_RED_PITCH + DK16 * (g * 4 + rr), v);
+          }
+      }
+      __syncthreads();
+      {
+        // 32 rows x DK columns summed over the 4 key blocks in wave order; thread -> (row, 8 columns).  The same thread owns the
+        // same dQ elements in every chunk: its load of the earlier chunks' sum follows its own store in program order.
+        constexpr int CPT = DK / 8;                                   // threads per row
+        const int q = threadIdx.x / CPT, d0 = (threadIdx.x % CPT) * 8;
+        if (q < 32 && q < Lq) {
+          float* out = dQ + ((int64_t)r * Lq + q) * lddq + h * DK + d0;
+          f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
+          if (c > 0) { a0 = *reinterpret_cast<const f32x4*>(out); a1 = *reinterpret_cast<const f32x4*>(out + 4); }
+          f32x4 b0 = f32x4{0.f, 0.f, 0.f, 0.f}, b1 = b0;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            const float* src = red + (w * 32 + q) * KB_RED_PITCH + d0;
+            const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
+            b0 += x0; b1 += x1;
+          }
+          *reinterpret_cast<f32x4*>(out) = a0 + b0;
+          *reinterpret_cast<f32x4*>(out + 4) = a1 + b1;
+        }
+      }
+      if (nk > 0) {
+        float aq[8][DK16], ao[8][DK16];
+        raw_q_cols<DK16>(aq, Qb, ldq, Lq, i, g);
+        raw_q_cols<DK16>(ao, dOb, lddo, Lq, i, g);
+        __builtin_amdgcn_sched_barrier(0);
+        mask_q_cols<DK16>(aq, Lq, g);
+        tile_to_lds<2>(T, KB_PITCH, dp, i, g);
+        contract_q_acc_regs<DK16, PR>(T, KB_PITCH, aq, accK, i, g);        // dK_blk += dS_blk^T Q
+        __builtin_amdgcn_sched_barrier(0);
+        mask_q_cols<DK16>(ao, Lq, g);
+        tile_to_lds<2>(T, KB_PITCH, p, i, g);
+        contract_q_acc_regs<DK16, PR>(T, KB_PITCH, ao, accV, i, g);        // dV_blk += P_blk^T dO
+      }
+    }
+    if (nk > 0) {
+      store_key_rows<DK16>(accK, dK + ((int64_t)kvr * Lk + k0) * lddk + h * DK, lddk, nk, i, g);
+      store_key_rows<DK16>(accV, dV + ((int64_t)kvr * Lk + k0) * lddv + h * DK, lddv, nk, i, g);
+    }
+  }
+}
+
 }  // namespace attn

@@ -11,8 +11,8 @@
 
 namespace {
 
-// shapes the register-resident MFMA attention covers; anything else (or NACF_ATTN_VALU=1)
-// takes the generic LDS/VALU kernels below
+// shapes the register-resident MFMA attention covers; cross-attention over more keys takes the streaming kernels
+// (attn_stream_ok), anything else (or NACF_ATTN_VALU=1) the generic LDS/VALU kernels below
 inline bool attn_mfma_ok(int Lq, int Lk, int dk) {
   const char* e = getenv("NACF_ATTN_VALU");
   if (e && atoi(e) != 0) return false;
@@ -28,6 +28,29 @@ inline int attn_precision(int dk) {
 }
 inline bool attn_aligned(const void* p, int64_t ld) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld % 4) == 0;
+}
+// memories of more than 128 keys: the streaming kernels (attn_mfma.hpp: fwd_stream_kernel, bwd_kb_stream_kernel).
+// NACF_ATTN_STREAM=0 restores the generic kernel (or its NACF_EUNSUPPORTED); =2 also sends memories of 33..128 keys there (tests)
+inline bool attn_stream_ok(int Lk, int dk, const int64_t* key_tokens, int causal, float p_drop) {
+  if (key_tokens || causal || dk != 64 || p_drop != 0.f) return false;
+  const char* v = getenv("NACF_ATTN_VALU");
+  if (v && atoi(v) != 0) return false;
+  const char* e = getenv("NACF_ATTN_STREAM");
+  const int mode = (e && *e) ? atoi(e) : 1;
+  return mode != 0 && (Lk > 128 || (mode == 2 && Lk > 32));
+}
+// A kernel's dynamic-LDS ceiling is an attribute of the function ON ONE DEVICE: raised once per (kernel, device), remembered per
+// device, and a failure is an error of the call.
+constexpr int ATTR_MAX_DEV = 64;
+template <typename Fn>
+int attn_raise_lds(Fn* fn, bool (&done)[ATTR_MAX_DEV], const char* what) {
+  int d = -1;
+  NACF_CHECK(hipGetDevice(&d) == hipSuccess, NACF_ELAUNCH, "%s: hipGetDevice failed", what);
+  if (d >= 0 && d < ATTR_MAX_DEV && done[d]) return NACF_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  NACF_CHECK(e == hipSuccess, NACF_ELAUNCH, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", what, hipGetErrorString(e));
+  if (d >= 0 && d < ATTR_MAX_DEV) done[d] = true;
+  return NACF_OK;
 }
 
 constexpr int EMB_THREADS = 128;
@@ -983,6 +1006,27 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
   NACF_CHECK(R > 0 && H > 0 && Lq > 0 && Lk > 0 && dk > 0 && kv_div > 0 && kv_mod > 0, NACF_EINVAL,
              "nacf_attention_fwd: bad shape");
   NACF_CHECK(!(causal && Lq != Lk), NACF_EINVAL, "nacf_attention_fwd: causal mask needs Lq == Lk");
+  if (attn_stream_ok(Lk, dk, key_tokens, causal, p_drop) && attn_aligned(Q, ldq) && attn_aligned(K, ldk) && attn_aligned(V, ldv) &&
+      attn_aligned(O, ldo)) {
+    // cross-attention over more than 128 keys: K / V streamed through LDS in blocks of FS_KEYS keys, running soft-max statistics
+    const int groups = cdiv(R, kv_div);
+    const int n_kv = kv_mod < groups ? kv_mod : groups;
+    const int nseq_max = kv_div * cdiv(groups, kv_mod);
+    const size_t lds = (size_t)2 * 2 * attn::FS_KEYS * attn::FL_PITCH * sizeof(float);   // two images of a K block and a V block
+    static bool set_fs[4][ATTR_MAX_DEV];
+#define NACF_ATTN_FS(PR, PROBS)                                                                                            \
+  do {                                                                                                                    \
+    if (int rc = attn_raise_lds(attn::fwd_stream_kernel<4, PR, PROBS>, set_fs[2 * PR + PROBS], "nacf_attention_fwd(mfma, stream)")) \
+      return rc;                                                                                                          \
+    hipLaunchKernelGGL((attn::fwd_stream_kernel<4, PR, PROBS>), dim3(n_kv * H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, \
+                       ldv, O, ldo, probs, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);                                  \
+  } while (0)
+    if (attn_precision(dk)) { if (probs) NACF_ATTN_FS(1, true); else NACF_ATTN_FS(1, false); }
+    else { if (probs) NACF_ATTN_FS(0, true); else NACF_ATTN_FS(0, false); }
+#undef NACF_ATTN_FS
+    NACF_LAUNCH_CHECK("nacf_attention_fwd(mfma, stream)");
+    return NACF_OK;
+  }
   // more than 32 queries per sequence run as blocks of 32 (one wave each) when no causal mask ties a query to its index
   // (probability dropout runs on the LDS-tile kernel below: the probabilities sit in LDS there, one mask multiply away)
   if (p_drop == 0.f && attn_mfma_ok(causal ? Lq : min(Lq, 32), Lk, dk) && attn_aligned(Q, ldq) && attn_aligned(K, ldk) &&
@@ -1031,7 +1075,12 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
     return NACF_OK;
   }
   const size_t lds = ((size_t)Lq * (dk + 1) + (size_t)Lk * (dk + 1) + (size_t)Lq * Lk) * sizeof(float);
-  NACF_CHECK(lds <= 160 * 1024, NACF_EUNSUPPORTED, "nacf_attention_fwd: tile does not fit LDS (%zu B)", lds);
+  // (what lands here: a key mask or a causal mask beyond 32 queries / 128 keys, dk other than 16 / 64, unaligned operands,
+  //  attention_probs_dropout_prob > 0, NACF_ATTN_VALU=1, NACF_ATTN_STREAM=0)
+  NACF_CHECK(lds <= 160 * 1024, NACF_EUNSUPPORTED,
+             "nacf_attention_fwd: the LDS-tile kernel needs (Lq*(dk+1) + Lk*(dk+1) + Lq*Lk) * 4 <= 163840 B of LDS, got %zu B "
+             "(Lq=%d Lk=%d dk=%d%s)", lds, Lq, Lk, dk,
+             p_drop > 0.f ? "; attention_probs_dropout_prob > 0 always runs on this kernel" : "");
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1063,8 +1112,28 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
              "nacf_attention_bwd: bad shape");
   NACF_CHECK(n_kv == kv_mod || (kv_div == 1 && kv_mod >= R && n_kv == R), NACF_EINVAL,
              "nacf_attention_bwd: n_kv must equal kv_mod (or R for the identity map)");
-  NACF_CHECK(Lk * dk <= ATT_BWD_MAXJ * 256, NACF_EUNSUPPORTED, "nacf_attention_bwd: Lk*dk > %d", ATT_BWD_MAXJ * 256);
   NACF_CHECK(!(causal && Lq != Lk), NACF_EINVAL, "nacf_attention_bwd: causal mask needs Lq == Lk");
+  if (Lq <= 32 && attn_stream_ok(Lk, dk, key_tokens, causal, p_drop) && attn_aligned(Q, ldq) && attn_aligned(K, ldk) &&
+      attn_aligned(V, ldv) && attn_aligned(dO, lddo) && attn_aligned(dQ, lddq) && attn_aligned(dK, lddk) && attn_aligned(dV, lddv)) {
+    // cross-attention over more than 128 keys: statistics pre-pass, then chunks of 128 keys with the key-block kernel's ownership
+    const int groups = cdiv(R, kv_div);
+    const int nseq_max = kv_div * cdiv(groups, kv_mod);
+    const size_t lds_ks = (size_t)(3 * 4 * 32 + 4 * 32 * attn::KB_RED_PITCH + 4 * 32 * attn::KB_PITCH + (size_t)nseq_max * 3 * 32) * sizeof(float);
+    if (lds_ks <= 160 * 1024) {                 // (more than 266 sequences per memory row set: the generic kernel's answer)
+      static bool set_ks[2][ATTR_MAX_DEV];
+      if (attn_precision(dk)) {
+        if (int rc = attn_raise_lds(attn::bwd_kb_stream_kernel<4, 1>, set_ks[1], "nacf_attention_bwd(mfma, stream)")) return rc;
+        hipLaunchKernelGGL((attn::bwd_kb_stream_kernel<4, 1>), dim3(n_kv * H), dim3(256), lds_ks, as_hip(stream), Q, ldq, K, ldk, V,
+                           ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+      } else {
+        if (int rc = attn_raise_lds(attn::bwd_kb_stream_kernel<4, 0>, set_ks[0], "nacf_attention_bwd(mfma, stream)")) return rc;
+        hipLaunchKernelGGL((attn::bwd_kb_stream_kernel<4, 0>), dim3(n_kv * H), dim3(256), lds_ks, as_hip(stream), Q, ldq, K, ldk, V,
+                           ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+      }
+      NACF_LAUNCH_CHECK("nacf_attention_bwd(mfma, stream)");
+      return NACF_OK;
+    }
+  }
   if (p_drop == 0.f && attn_mfma_ok(Lq, Lk, dk) && attn_aligned(Q, ldq) && attn_aligned(K, ldk) && attn_aligned(V, ldv) &&
       attn_aligned(dO, lddo) && attn_aligned(dQ, lddq) && attn_aligned(dK, lddk) && attn_aligned(dV, lddv)) {
     // sequences per memory row set (upper bound) -> waves per item (1, 2 or 4) and rounds of the item loop
@@ -1129,7 +1198,13 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
     return NACF_OK;
   }
   const size_t lds = ((size_t)2 * Lq * (dk + 1) + (size_t)2 * Lk * (dk + 1) + (size_t)2 * Lq * Lk) * sizeof(float);
-  NACF_CHECK(lds <= 160 * 1024, NACF_EUNSUPPORTED, "nacf_attention_bwd: tile does not fit LDS (%zu B)", lds);
+  // the LDS-tile kernel keeps a thread's dK / dV elements in ATT_BWD_MAXJ registers and every operand of a row set in LDS
+  NACF_CHECK(Lk * dk <= ATT_BWD_MAXJ * 256, NACF_EUNSUPPORTED,
+             "nacf_attention_bwd: the LDS-tile kernel needs Lk*dk <= %d, got Lk=%d dk=%d (Lq=%d%s)", ATT_BWD_MAXJ * 256, Lk, dk, Lq,
+             p_drop > 0.f ? "; attention_probs_dropout_prob > 0 always runs on this kernel" : "");
+  NACF_CHECK(lds <= 160 * 1024, NACF_EUNSUPPORTED,
+             "nacf_attention_bwd: the LDS-tile kernel needs (2*Lq*(dk+1) + 2*Lk*(dk+1) + 2*Lq*Lk) * 4 <= 163840 B of LDS, got %zu B "
+             "(Lq=%d Lk=%d dk=%d)", lds, Lq, Lk, dk);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
