@@ -64,7 +64,7 @@ int nacf_version(void);
  * included).  nacf_abi_count() returns the value the LIBRARY was built with; the ctypes loader
  * (runtime/lib.py:load) refuses a library whose count differs from its own signature table, so a stale
  * libnacf_hip.so next to a newer Python package fails at import time, not at the first missing symbol. */
-#define NACF_ABI_COUNT 92
+#define NACF_ABI_COUNT 93
 int nacf_abi_count(void);
 
 /* ---- batch construction (reference: dataloader.py) ----------------------------------------
@@ -475,7 +475,9 @@ int nacf_attention_fwd(const float* Q, int64_t ldq, const float* K, int64_t ldk,
                        int R, int H, int Lq, int Lk, int dk, int kv_div, int kv_mod,
                        nacf_stream_t stream);
 /* dQ [R,Lq,*], dK/dV [n_kv, Lk, *]; each kv row sums, in a fixed order, the
- * contributions of the query rows mapped to it. */
+ * contributions of the query rows mapped to it.  A query row all of whose keys are filled (every key <pad>, or every key
+ * its causal / watch window leaves it) has scores made of masked_fill's constants only (models/bert.py:160): as in autograd
+ * it gets dQ = 0 and adds nothing to dK; its uniform P still feeds dV. */
 int nacf_attention_bwd(const float* Q, int64_t ldq, const float* K, int64_t ldk,
                        const float* V, int64_t ldv, const float* dO, int64_t lddo,
                        float* dQ, int64_t lddq, float* dK, int64_t lddk, float* dV, int64_t lddv,
@@ -498,6 +500,14 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
                                const int64_t* key_tokens, int causal,
                                int R, int n_kv, int H, int Lq, int Lk, int dk, int kv_div, int kv_mod,
                                float p_drop, uint32_t salt, const uint64_t* rng_state, nacf_stream_t stream);
+/* template name of the attention kernel the calling thread launched last through any of the four entry points above
+ * (the instantiation as the dispatch spells it: "fwd_kernel<8, 4, 0>", "fwd_lds_kernel<4, 1>",
+ * "fwd_stream_kernel<4, 0, probs>" | "<4, 0, no probs>", "bwd_kernel<2, 1, 0> wpi=2", "bwd_kb_kernel<4>" | "<4, 0>" | "<4, 1, 1>",
+ * "bwd_kb_stream_kernel<4, 0>", "attention_fwd_kernel", "attention_bwd_kernel"; "" before the first call).
+ * A diagnostic for tests: the dispatch of models/bert.py:157-179's one soft-max(Q K^T) V onto the instantiations of
+ * csrc/attn_mfma.hpp has silent fall-throughs (alignment, sequences per memory, environment switches).  A pointer to a
+ * string literal: nothing is formatted on the launch path. */
+const char* nacf_attention_last_kernel(void);
 
 /* masked row mean of the last layer (the `embs` output, models/bert.py:301):
  * out[r,:] = sum_l y[r,l,:] / count(tokens[r,:] != PAD) */

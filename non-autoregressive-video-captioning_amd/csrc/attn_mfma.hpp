@@ -92,9 +92,9 @@ __device__ __forceinline__ void load_row_frag(f32x4 (&f)[DK16], const float* __r
   constexpr int DK = 16 * DK16;
 #if NACF_ATTN_BF_ROWFRAG
   // a guarded load is a basic block of its own, and loads in different blocks are never batched: every fragment then costs one full
-  // L2 latency.  Read the last live row instead (n_rows >= 1) and replace the value by zero.
+  // L2 latency.  Read the last live row instead (row 0 when a caller passes n_rows = 0 to blank a row) and replace the value by zero.
   const bool live = row < n_rows;
-  const float* src = base + (int64_t)(live ? row : n_rows - 1) * ld + g * (DK / 4);
+  const float* src = base + (int64_t)(live ? row : (n_rows > 0 ? n_rows - 1 : 0)) * ld + g * (DK / 4);
 #pragma unroll
   for (int j = 0; j < DK16; ++j) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * j);
@@ -202,9 +202,10 @@ __device__ __forceinline__ void store_rows(const f32x4 (&o)[2][DK16], float* __r
 
 // scores (accumulator layout) -> probabilities, in place.  Mirrors models/bert.py:157-167:
 // divide by sqrt(dk) AFTER the product, masked_fill(-10e6), softmax over keys.
+// all_pad (backward): bit tm is set when every key of query row 16*tm + i is <pad> -- the row maximum is then the fill value itself.
 template <int NKT, bool FWD = false>
 __device__ __forceinline__ void softmax_rows(f32x4 (&s)[2][NKT], float sq, const int64_t* __restrict__ key_tok,
-                                             int causal, int Lk, int i, int g) {
+                                             int causal, int Lk, int i, int g, unsigned* all_pad = nullptr) {
   unsigned long long padbits = 0ull;  // bit (tn*4+rr): key is PAD or beyond Lk handled separately
   if (key_tok) {
 #if NACF_ATTN_KEYTOK_BALLOT
@@ -255,6 +256,7 @@ __device__ __forceinline__ void softmax_rows(f32x4 (&s)[2][NKT], float sq, const
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (all_pad && key_tok && mx == -10e6f) *all_pad |= 1u << tm;
     float sum = 0.f;
 #pragma unroll
     for (int tn = 0; tn < NKT; ++tn)
@@ -475,11 +477,15 @@ __global__ __launch_bounds__(256) void bwd_kernel(const float* __restrict__ Q, i
         for (int tm = 0; tm < 2; ++tm) load_row_frag<DK16>(qf[tm], Qb, ldq, tm * 16 + i, Lq, g);
         contract_d<NKT, DK16, PR>(p, Kb, ldk, Lk, qf, i, g);
       }
-      softmax_rows<NKT>(p, sq, key_tokens ? key_tokens + (int64_t)r * Lk : nullptr, causal, Lk, i, g);
+      unsigned all_pad = 0u;
+      softmax_rows<NKT>(p, sq, key_tokens ? key_tokens + (int64_t)r * Lk : nullptr, causal, Lk, i, g, &all_pad);
       {
+        // A query row whose keys are all <pad> runs its soft-max over masked_fill's constants (models/bert.py:160-161): no gradient
+        // reaches Q K^T.  Its dO fragment reads as zero HERE (dP = 0, delta = 0, dS = 0 exactly: dQ = 0, nothing added to dK); dV
+        // below takes dO from memory and keeps P^T dO.  Rows with a live key are untouched: P is exactly 0 at their filled keys.
         f32x4 gf[2][DK16];
 #pragma unroll
-        for (int tm = 0; tm < 2; ++tm) load_row_frag<DK16>(gf[tm], dOb, lddo, tm * 16 + i, Lq, g);
+        for (int tm = 0; tm < 2; ++tm) load_row_frag<DK16>(gf[tm], dOb, lddo, tm * 16 + i, ((all_pad >> tm) & 1u) ? 0 : Lq, g);
         contract_d<NKT, DK16, PR>(dp, Vb, ldv, Lk, gf, i, g);   // dP = dO V^T
       }
       // dS = P * (dP - rowsum(P * dP)) / sqrt(dk)

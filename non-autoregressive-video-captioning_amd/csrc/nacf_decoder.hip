@@ -26,6 +26,8 @@ inline int attn_precision(int dk) {
   if (e && *e) return atoi(e) != 0 ? 1 : 0;
   return nacf_gemm_get_mode() == NACF_GEMM_BF16 ? 1 : 0;
 }
+// nacf_attention_last_kernel(): the instantiation the calling thread launched last -- a pointer to a literal, set per dispatch branch
+thread_local const char* g_attn_last_kernel = "";
 inline bool attn_aligned(const void* p, int64_t ld) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld % 4) == 0;
 }
@@ -783,6 +785,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
       float s = 0.f;
       for (int k = lane; k < Lk; k += 64) { const float e = expf(row[k] - m); row[k] = e; s += e; }
       s = wave_sum(s);
+      // every key of the row is <pad>: the soft-max runs over masked_fill's constants (models/bert.py:160-161), which pass no
+      // gradient to Q K^T -- P (uniform) still feeds dV.  Only then is P non-zero at a filled key, so no per-key select is needed.
+      const bool dead = key_tokens && m == -10e6f;
       float dotp = 0.f;
       if (p_drop > 0.f) {
         // O = (P o M) V with M = keep / (1 - p): dP = (dO V^T) o M, the soft-max backward runs on the undropped P, dV on P o M
@@ -797,14 +802,14 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
         dotp = wave_sum(dotp);
         for (int k = lane; k < Lk; k += 64) {
           const float p = row[k];
-          drow[k] = p * (drow[k] - dotp) / sq;
+          drow[k] = dead ? 0.f : p * (drow[k] - dotp) / sq;
           row[k] = p * rng.keep1(e0 + k, salt, p_drop);
         }
         continue;
       }
       for (int k = lane; k < Lk; k += 64) { const float p = row[k] / s; row[k] = p; dotp += p * drow[k]; }
       dotp = wave_sum(dotp);
-      for (int k = lane; k < Lk; k += 64) drow[k] = row[k] * (drow[k] - dotp) / sq;  // grad wrt Q.K^T
+      for (int k = lane; k < Lk; k += 64) drow[k] = dead ? 0.f : row[k] * (drow[k] - dotp) / sq;  // grad wrt Q.K^T
     }
     __syncthreads();
     for (int idx = tid; idx < Lq * dk; idx += 256) {
@@ -996,6 +1001,8 @@ int nacf_masked_mean_fwd(const float* y, const int64_t* tokens, float* out, int 
   return NACF_OK;
 }
 
+const char* nacf_attention_last_kernel(void) { return g_attn_last_kernel; }
+
 int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv, float* O,
                                int64_t ldo, const int64_t* key_tokens, int causal, float* probs, int R, int H, int Lq, int Lk,
                                int dk, int kv_div, int kv_mod, float p_drop, uint32_t salt, const uint64_t* rng_state,
@@ -1020,6 +1027,7 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
       return rc;                                                                                                          \
     hipLaunchKernelGGL((attn::fwd_stream_kernel<4, PR, PROBS>), dim3(n_kv * H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, \
                        ldv, O, ldo, probs, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);                                  \
+    g_attn_last_kernel = PROBS ? "fwd_stream_kernel<4, " #PR ", probs>" : "fwd_stream_kernel<4, " #PR ", no probs>";        \
   } while (0)
     if (attn_precision(dk)) { if (probs) NACF_ATTN_FS(1, true); else NACF_ATTN_FS(1, false); }
     else { if (probs) NACF_ATTN_FS(0, true); else NACF_ATTN_FS(0, false); }
@@ -1050,12 +1058,15 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
           set_fl = true;
         }
-        if (attn_precision(dk))
+        if (attn_precision(dk)) {
           hipLaunchKernelGGL((attn::fwd_lds_kernel<4, 1>), dim3(n_kv * H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, ldv,
                              O, ldo, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
-        else
+          g_attn_last_kernel = "fwd_lds_kernel<4, 1>";
+        } else {
           hipLaunchKernelGGL((attn::fwd_lds_kernel<4>), dim3(n_kv * H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, ldv,
                              O, ldo, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+          g_attn_last_kernel = "fwd_lds_kernel<4, 0>";
+        }
         NACF_LAUNCH_CHECK("nacf_attention_fwd(mfma, lds)");
         return NACF_OK;
       }
@@ -1065,8 +1076,11 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
     const dim3 grid(cdiv(R * H * nqb, 4));
     hipStream_t s = as_hip(stream);
 #define NACF_ATTN_FWD(NKT, DK16, PR)                                                                                      \
-  hipLaunchKernelGGL((attn::fwd_kernel<NKT, DK16, PR>), grid, dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, key_tokens, \
-                     causal, probs, R, H, Lq, Lk, kv_div, kv_mod, nqb)
+  do {                                                                                                                    \
+    hipLaunchKernelGGL((attn::fwd_kernel<NKT, DK16, PR>), grid, dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, key_tokens, \
+                       causal, probs, R, H, Lq, Lk, kv_div, kv_mod, nqb);                                                 \
+    g_attn_last_kernel = "fwd_kernel<" #NKT ", " #DK16 ", " #PR ">";                                                      \
+  } while (0)
     const int pr = attn_precision(dk);
     if (Lk <= 32) { if (dk == 64) { if (pr) NACF_ATTN_FWD(2, 4, 1); else NACF_ATTN_FWD(2, 4, 0); } else NACF_ATTN_FWD(2, 1, 0); }
     else { if (dk == 64) { if (pr) NACF_ATTN_FWD(8, 4, 1); else NACF_ATTN_FWD(8, 4, 0); } else NACF_ATTN_FWD(8, 1, 0); }
@@ -1089,6 +1103,7 @@ int nacf_attention_fwd_dropout(const float* Q, int64_t ldq, const float* K, int6
   }
   hipLaunchKernelGGL(attention_fwd_kernel, dim3(R, H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, ldv, O, ldo,
                      key_tokens, causal, probs, R, Lq, Lk, dk, kv_div, kv_mod, p_drop, salt, rng_state);
+  g_attn_last_kernel = "attention_fwd_kernel";
   NACF_LAUNCH_CHECK("nacf_attention_fwd");
   return NACF_OK;
 }
@@ -1125,10 +1140,12 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
         if (int rc = attn_raise_lds(attn::bwd_kb_stream_kernel<4, 1>, set_ks[1], "nacf_attention_bwd(mfma, stream)")) return rc;
         hipLaunchKernelGGL((attn::bwd_kb_stream_kernel<4, 1>), dim3(n_kv * H), dim3(256), lds_ks, as_hip(stream), Q, ldq, K, ldk, V,
                            ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+        g_attn_last_kernel = "bwd_kb_stream_kernel<4, 1>";
       } else {
         if (int rc = attn_raise_lds(attn::bwd_kb_stream_kernel<4, 0>, set_ks[0], "nacf_attention_bwd(mfma, stream)")) return rc;
         hipLaunchKernelGGL((attn::bwd_kb_stream_kernel<4, 0>), dim3(n_kv * H), dim3(256), lds_ks, as_hip(stream), Q, ldq, K, ldk, V,
                            ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+        g_attn_last_kernel = "bwd_kb_stream_kernel<4, 0>";
       }
       NACF_LAUNCH_CHECK("nacf_attention_bwd(mfma, stream)");
       return NACF_OK;
@@ -1156,15 +1173,19 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
           set_kb = true;
         }
-        if (e && atoi(e) == 2)
+        if (e && atoi(e) == 2) {
           hipLaunchKernelGGL((attn::bwd_kb_kernel<4, 0>), dim3(n_kv * H), dim3(256), lds_kb, as_hip(stream), Q, ldq, K, ldk, V,
                              ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
-        else if (attn_precision(dk))
+          g_attn_last_kernel = "bwd_kb_kernel<4, 0>";
+        } else if (attn_precision(dk)) {
           hipLaunchKernelGGL((attn::bwd_kb_kernel<4, 1, 1>), dim3(n_kv * H), dim3(256), lds_kb, as_hip(stream), Q, ldq, K, ldk, V,
                              ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
-        else
+          g_attn_last_kernel = "bwd_kb_kernel<4, 1, 1>";
+        } else {
           hipLaunchKernelGGL((attn::bwd_kb_kernel<4>), dim3(n_kv * H), dim3(256), lds_kb, as_hip(stream), Q, ldq, K, ldk, V,
                              ldv, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, R, n_kv, H, Lq, Lk, kv_div, kv_mod, nseq_max);
+          g_attn_last_kernel = "bwd_kb_kernel<4>";
+        }
         NACF_LAUNCH_CHECK("nacf_attention_bwd(mfma, key blocks)");
         return NACF_OK;
       }
@@ -1189,6 +1210,9 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
     hipLaunchKernelGGL((attn::bwd_kernel<NKT, DK16, PR>), grid, dim3(256), lds_m, s, Q, ldq, K, ldk, V, ldv, dO, lddo, \
                        dQ, lddq, dK, lddk, dV, lddv, key_tokens, causal, R, n_kv, H, Lq, Lk, kv_div, kv_mod, wpi,      \
                        rounds);                                                                                       \
+    g_attn_last_kernel = wpi == 1   ? "bwd_kernel<" #NKT ", " #DK16 ", " #PR "> wpi=1"                                \
+                         : wpi == 2 ? "bwd_kernel<" #NKT ", " #DK16 ", " #PR "> wpi=2"                                \
+                                    : "bwd_kernel<" #NKT ", " #DK16 ", " #PR "> wpi=4";                               \
   } while (0)
     const int pr = attn_precision(dk);
     if (nkt == 2) { if (dk == 64) { if (pr) NACF_ATTN_BWD(2, 4, 1); else NACF_ATTN_BWD(2, 4, 0); } else NACF_ATTN_BWD(2, 1, 0); }
@@ -1213,6 +1237,7 @@ int nacf_attention_bwd_dropout(const float* Q, int64_t ldq, const float* K, int6
   }
   hipLaunchKernelGGL(attention_bwd_kernel, dim3(n_kv, H), dim3(256), lds, as_hip(stream), Q, ldq, K, ldk, V, ldv, dO, lddo,
                      dQ, lddq, dK, lddk, dV, lddv, key_tokens, causal, R, Lq, Lk, dk, kv_div, kv_mod, p_drop, salt, rng_state);
+  g_attn_last_kernel = "attention_bwd_kernel";
   NACF_LAUNCH_CHECK("nacf_attention_bwd");
   return NACF_OK;
 }

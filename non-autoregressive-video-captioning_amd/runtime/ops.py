@@ -952,6 +952,11 @@ def attention_bwd(q, k, v, do, dq, dk_, dv, key_tokens, causal, R, n_kv, H, Lq, 
                                         dk, kv_div, kv_mod, _stream()), "nacf_attention_bwd")
 
 
+def attention_last_kernel() -> str:
+    """template name of the attention kernel this thread launched last (nacf_attention_last_kernel; "" before the first call)"""
+    return (L.load().nacf_attention_last_kernel() or b"").decode()
+
+
 def masked_mean_fwd(y, tokens, out):
     _chk_f32(y, out)
     R, Lq, D = y.shape
